@@ -8,11 +8,17 @@ the 256^3 system; the matrix and right-hand side are generated and assembled
 on the GPUs before timing (synthetic data).  Work per step is
 fixed across N (strong scaling): value = K / max-over-ranks(time of K steps).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 256] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
-The timed solve runs with rtol = 0 so exactly K iterations execute; the
-converged solve (default rtol 1e-5) is reported separately as time-to-solution.
+The timed solve runs with rtol = 0 so exactly K iterations execute.  A plain
+run does only what the headline needs: set-up, W warm-up iterations, the K
+timed ones, the outputs (--dump-outputs) and the line.  --full adds everything
+else the line can carry: the converged solve (default rtol 1e-5, reported as
+time-to-solution) and its parity check against the oracle, the CPU baseline,
+the roofline pass, the standalone and cold MatMult, the host-assembly,
+streamed-values, random-pattern and C2 / C4 / C5-share legs and, at N > 1, the
+alternative legs beside the library's default.
 Rank 0 prints one JSON line.
 """
 from __future__ import annotations
@@ -782,12 +788,40 @@ def parity_record(its: int, reason: int, rel: float, o: dict) -> dict:
             "ok": int(its) == o["its"] and int(reason) == o["reason"] and rel <= 1e-10}
 
 
+DUMP_MAX_ROWS = 1 << 22   # 32 MB of fp64: a longer solution is dumped as a seeded sample of its rows
+
+
+def dump_rows(M: int):
+    """The global rows of x that --dump-outputs writes: None (all of them) when
+    M <= DUMP_MAX_ROWS, else a fixed sample of DUMP_MAX_ROWS rows (seed 0, drawn
+    with replacement, ascending) -- the same rows in every run and at every N."""
+    if M <= DUMP_MAX_ROWS:
+        return None
+    import numpy as np
+    return np.sort(np.random.default_rng(0).integers(0, M, size=DUMP_MAX_ROWS, dtype=np.int64))
+
+
+def write_outputs(path: str, x_parts: list, rnorm: float) -> None:
+    """DIR/x.npy: the solution vector the timed solve left after its K-th
+    iteration (the rows of dump_rows, the ranks' parts in rank order), fp64;
+    DIR/rnorm.npy: the residual norm that solve returned, fp64, shape (1,)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "x.npy"), np.concatenate(x_parts).astype(np.float64, copy=False))
+    np.save(os.path.join(path, "rnorm.npy"), np.array([rnorm], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--grid", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left (x, rnorm) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (converged solve + parity, CPU baseline, roofline "
+                         "pass, standalone MatMult, the other legs and configurations); the --no-* options trim it")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-solve", action="store_true", help="skip the converged solves and the parity check")
     ap.add_argument("--no-asm", action="store_true", help="skip the createAIJ-from-host-arrays leg")
@@ -801,6 +835,8 @@ def main():
         threads, how = cpu_threads()
         print(json.dumps(cpu_baseline_config(args.cpu_config, threads, how)), flush=True)
         return
+    if not args.full:       # a plain run: none of the legs beside the headline
+        args.no_cpu = args.no_solve = args.no_asm = args.no_general = args.no_random = args.no_configs = True
 
     import numpy as np
     import torch
@@ -882,6 +918,12 @@ def main():
     b = comm.empty(m)
     rhs_hash(comm, info["rstart"], b)
     x = comm.zeros(m)
+    dump_sel = None             # this rank's share of the rows --dump-outputs writes (None: all)
+    if args.dump_outputs:
+        rows = dump_rows(info["M"])
+        if rows is not None:
+            rows = rows[(rows >= info["rstart"]) & (rows < info["rstart"] + m)] - info["rstart"]
+            dump_sel = torch.from_numpy(rows).to(x.device)
 
     # first solve on the fresh operator pays PCSetUp_Jacobi (diagonal, the
     # uniform-diagonal test) and KSPSetUp (work space): time it against a repeat
@@ -904,7 +946,7 @@ def main():
     # between barrier + sync on both sides (rtol = 0 never stops early), max
     # over ranks; then the leg's converged solve (default tolerances) whose
     # its, reason and x are checked against the oracle below.
-    if world == 1:
+    if world == 1 or not args.full:     # (a plain run at N > 1: the library's default only)
         leg_specs = [("auto", {})]
     else:
         # the library's default first ("auto": CG mode 5 with the direction
@@ -943,6 +985,8 @@ def main():
                "value": round(args.steps / dt, 3),
                "ms_per_step": round(dt / args.steps * 1e3, 4), "_dt": dt,
                "per_rank_timed_s": [round(v, 5) for v in gather(dt_local)]}
+        if args.dump_outputs:               # what the K-th timed step left, before anything overwrites x
+            leg["_out"] = ((x if dump_sel is None else x[dump_sel]).cpu().numpy(), float(r["rnorm"]))
         if not args.no_solve:
             x.zero_()
             barrier()
@@ -992,6 +1036,13 @@ def main():
     chosen = choose_leg(legs, args.no_solve)
     set_knobs(chosen["knobs"])          # the chosen leg's settings for the measurements below
     value, dt = chosen["value"], chosen["_dt"]
+    if args.dump_outputs:       # the leg `value` comes from; rank 0 writes every rank's rows
+        parts = gather(chosen["_out"][0])
+        if rank == 0:
+            write_outputs(args.dump_outputs, parts, chosen["_out"][1])
+        del parts
+        for lg in legs:
+            lg.pop("_out", None)
     legs += failed
 
     mode, xb = chosen["cg_mode"], chosen.get("cg_xbatch", 1)
@@ -999,7 +1050,7 @@ def main():
     bytes_spmv = spmv_format_bytes(info, m, nnz_loc, ng)
     pw = dom = comm_lat = None
     achieved = avg_ms = spmv_avg_ms = spmv_alone_ms = mult_ms = cold_ms = cold_kernel_ms = bytes_launch = None
-    if comm_dead is None:       # (an aborted communicator runs nothing more)
+    if args.full and comm_dead is None:       # (an aborted communicator runs nothing more)
         # roofline pass: the same CG iterations with a HIP event pair on every
         # MatMult-family launch (on the library stream the kernel runs on; one
         # rank: the events are attached to the kernel's own dispatch by
@@ -1081,7 +1132,7 @@ def main():
                  "time_to_solution_s": round(ts + t_asm + t_setup, 3),
                  "process_init_s": round(t_init, 3)}
 
-    copy_gbps = round(stream_copy_gbps(x.device, m), 1) if comm_dead is None else None
+    copy_gbps = round(stream_copy_gbps(x.device, m), 1) if args.full and comm_dead is None else None
 
     asm_host = None
     if rank == 0 and world == 1 and not args.no_asm:

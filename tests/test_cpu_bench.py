@@ -102,6 +102,24 @@ def test_multi_gpu_legs_start_with_the_default():
     assert bench_parse_stall_ok()
 
 
+def test_dump_rows_fixed_sample_and_files(tmp_path):
+    """--dump-outputs: a short solution is written whole, a long one as the
+    same seeded rows in every run (at most 64 MB in all), as fp64 .npy files
+    in rank order."""
+    import numpy as np
+    import bench
+    assert bench.dump_rows(bench.DUMP_MAX_ROWS) is None
+    a, b = bench.dump_rows(256 ** 3), bench.dump_rows(256 ** 3)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_MAX_ROWS and 8 * a.size + 8 <= 64 << 20
+    assert a.dtype == np.int64 and a.min() >= 0 and a.max() < 256 ** 3 and np.all(np.diff(a) >= 0)
+    d = str(tmp_path / "out")
+    bench.write_outputs(d, [np.arange(3.0), np.arange(3.0, 5.0)], 0.25)
+    x, rn = np.load(os.path.join(d, "x.npy")), np.load(os.path.join(d, "rnorm.npy"))
+    assert x.dtype == rn.dtype == np.float64
+    assert np.array_equal(x, np.arange(5.0)) and np.array_equal(rn, [0.25])
+    assert sorted(os.listdir(d)) == ["rnorm.npy", "x.npy"]
+
+
 def bench_parse_stall_ok():
     import bench
     return bench.parse_stall("mode2/eager:20") == ("mode2/eager", 20.0) and bench.parse_stall(None) is None

@@ -12,9 +12,10 @@
 #   suite            the whole GPU test suite (as the driver runs it)
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench20          bench.py --steps 20 --warmup 5 (the driver's K/W class)
-#   bench            bench.py with its defaults (K = 500)
-#   benchfast        bench.py --steps 100 --no-cpu --no-asm --no-general
+#   bench20          bench.py --full --steps 20 --warmup 5 (every leg of the line at a short K)
+#   bench            bench.py --full with its defaults (K = 500)
+#   benchfast        bench.py --full --steps 100 --no-cpu --no-asm --no-general
+#   benchplain       bench.py --steps 20 --warmup 5 (the headline only)
 #   shm2             N = 2 rehearsal on one GPU (MXSOLVE_TRANSPORT=shm, torchrun)
 #   shm2fail         the same with the mode2/graph leg failing (the line must still print)
 #   shm2stall        the same with rank 1 stalling 40 s in the mode2/eager leg under an 8-s leg
@@ -59,16 +60,17 @@ for step in "$@"; do
     suite) run suite 1100 python3 -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread --durations=20 ;;
     tests:*) run "tests_${step#tests:}" 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${step#tests:}" ;;
     smoke) run smoke 400 python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench20) run bench20 500 python3 -u bench.py --steps 20 --warmup 5 ;;
-    bench) run bench 500 python3 -u bench.py ;;
-    benchfast) run benchfast 300 python3 -u bench.py --steps 100 --no-cpu --no-asm --no-general ;;
+    bench20) run bench20 500 python3 -u bench.py --full --steps 20 --warmup 5 ;;
+    bench) run bench 500 python3 -u bench.py --full ;;
+    benchfast) run benchfast 300 python3 -u bench.py --full --steps 100 --no-cpu --no-asm --no-general ;;
+    benchplain) run benchplain 120 python3 -u bench.py --steps 20 --warmup 5 ;;
     shm2) MXSOLVE_TRANSPORT=shm run shm2 400 python3 -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-            --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 50 --warmup 5 ;;
+            --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 50 --warmup 5 ;;
     shm2fail) MXSOLVE_TRANSPORT=shm MXSOLVE_BENCH_FAIL_LEG=mode2/graph run shm2fail 400 python3 -u -m torch.distributed.run \
-                --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 50 --warmup 5 ;;
+                --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --full --steps 50 --warmup 5 ;;
     shm2stall) MXSOLVE_TRANSPORT=shm MXSOLVE_BENCH_LEG_BUDGET_S=${BUDGET:-8} MXSOLVE_BENCH_STALL_LEG=mode2/eager:40 \
                  run shm2stall 400 python3 -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --steps 50 --warmup 5 ;;
+                 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --full --steps 50 --warmup 5 ;;
     prof) run prof 1000 bash tools/profile.sh ;;
     configs) run configs 700 python3 -u tools/bench_configs.py ;;
     c4prof) run c4prof 600 rocprofv3 --kernel-trace --stats -f csv -d $O/${TAG}_c4trace -o run -- \

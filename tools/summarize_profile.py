@@ -73,7 +73,7 @@ def main():
     spmv_alg = 8 * m + 8 * (m + ghosts) + 8 * m + 16 * ((m + 63) // 64) + (12 * ghosts + 4 * (m + 1) if ghosts else 0)
     alg = spmv_alg + 32 * m          # SPMV_CG: + r read, x read/write, p_i write
     out = {}
-    lines = [f"# {tag}: rocprofv3 summary (3D 7-pt Poisson {grid}^3, N={ngpu}, bench.py --steps 50)", "",
+    lines = [f"# {tag}: rocprofv3 summary (3D 7-pt Poisson {grid}^3, N={ngpu}, bench.py --full --steps 50)", "",
              "| kernel | calls | working launches | mean us (working) | median us (working) | % time | FETCH_SIZE KB (raw, median) | WRITE_SIZE KB (median) |",
              "|---|---|---|---|---|---|---|---|"]
     for r in stats[:14]:
@@ -157,7 +157,7 @@ def main():
             lines += [f"{k} per launch ({key}): FETCH_SIZE {fr/1e6:.1f} MB raw x {corr:.3f} + WRITE_SIZE "
                       f"{wr/1e6:.1f} MB = {t/1e6:.1f} MB vs {a/1e6:.1f} MB algorithmic ({t/a:.3f}x)."]
     lines += ["", "Produced by: `bash tools/gpu_run.sh <tag> prof` (tools/profile.sh: rocprofv3 --kernel-trace --stats, "
-              "then --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of `bench.py --steps 50 --warmup 5 --no-cpu "
+              "then --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of `bench.py --full --steps 50 --warmup 5 --no-cpu "
               "--no-solve --no-asm`, and the tools/calib_stream.py calibration pass), then "
               f"`python tools/summarize_profile.py {src} {tag} {grid} {ngpu}`."]
     with open(os.path.join(dst, f"{tag}_summary.md"), "w") as f:
