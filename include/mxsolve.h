@@ -358,9 +358,9 @@ int mx_lu_solve_csr(mx_comm c, int64_t n, const int64_t *indptr, const int64_t *
  *         stores the centre rows' (the iterations between x-step batches;
  *         the batch iterations keep the separate passes) -- the same bits as
  *         the separate direction update + PW pass: 0 off, 1 on, 5 (default)
- *         by size: 7-point up to 2^23 rows (128^3 -20% per iteration, 2^23
- *         -8%; 256^3 +2%: the residual update after it slows by more than it
- *         saves), 5-point up to 2^24 (2048^2 -14%, C2's 4096^2 -1.7%)
+ *         by size: up to 2^24 rows (7-point with key 85's shared form: 128^3
+ *         -16% per iteration, 256^3 -1.3 to -2.4%; 5-point: 2048^2 -14%,
+ *         C2's 4096^2 -1.7%)
  * key 70: the 27-point plane-pipelined z-march with two lines per wave (the
  *         column words pair up by lines: line y's dy = +1 run is line y + 1's
  *         centre run, 8 loads per plane for two units instead of 12; the same
@@ -390,6 +390,12 @@ int mx_lu_solve_csr(mx_comm c, int64_t n, const int64_t *indptr, const int64_t *
  *         general SELL block of >= 2^20 rows with half its entries or more
  *         2^17 columns or further from the diagonal, 2 for every general
  *         block (tests), 0 never; the same bits as the one-pass kernel
+ * key 85: the 7-point fused pass of key 69 passes each plane's centre p_i
+ *         between the four waves of a workgroup through LDS in place of the
+ *         loads that formed the +n and +1 operands again (columns per plane a
+ *         multiple of 4, lines of 1, 2 or a multiple of 4 units; every other
+ *         layout keeps the unshared kernel): 1 on (default), 0 off; the same
+ *         bits (256^3 175.9 -> 173.7 us per iteration)
  * (key 18, physically contiguous allocations, was retired in round 6: freed
  *  contiguous blocks whose address range was reused were still reached through
  *  stale translations -- DESIGN.md section 12.1)
@@ -407,8 +413,9 @@ int mx_debug_set(int key, int value);
  * CG mode 5's p.Ap and residual-update z-march passes, 13 / 14 coded z-march
  * (split: ghost units), 15 CG mode 5's direction update fused into the p.Ap
  * pass (key 69), 16 the same fused into the split p.Ap pass on P > 1 ranks
- * (key 80), 17 the column-block two-pass MatMult (key 84).  Writes min(n, 18)
- * counts; reset != 0
+ * (key 80), 17 the column-block two-pass MatMult (key 84), 18 a CG mode 5
+ * z-march launch that ran a shared form (key 85; counted beside its pass's
+ * kind).  Writes min(n, 19) counts; reset != 0
  * zeroes them.  Not a PETSc call: it lets the parity tests show which
  * kernel ran (replayed graph launches are not counted).                     */
 int mx_debug_dispatch_counts(int64_t *out, int n, int reset);

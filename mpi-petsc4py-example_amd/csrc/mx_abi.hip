@@ -685,6 +685,7 @@ int mx_debug_set(int key, int value) {
     case 80: old = g_knobs.cg_pbws; g_knobs.cg_pbws = value; break;
     case 81: old = g_knobs.scratch_cache; g_knobs.scratch_cache = value; if (!value) scratch_trim(); break;
     case 84: old = g_knobs.cb; g_knobs.cb = value; break;
+    case 85: old = g_knobs.zm_shared; g_knobs.zm_shared = value; break;
     case 69: old = g_knobs.cg_pbw; g_knobs.cg_pbw = value; break;
     case 68: old = g_knobs.ru_2line; g_knobs.ru_2line = value; break;
     case 61: old = g_knobs.gm_stall_us; g_knobs.gm_stall_us = std::min(std::max(value, 0), 2000000); break;

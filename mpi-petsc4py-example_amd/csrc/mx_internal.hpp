@@ -291,7 +291,7 @@ struct Knobs {
   int pair_lean = 1; int pair_zm = 1; int pair_zm_bpc = 4; int pair_zm_len = 32; int spmv_fp64_grid = 8192;
   int comm_wait_ms = 600000; int pair_col27 = 1; int pair_zmc = 1; int pair_unitv = 1; int pw_sym27 = 1;
   int pair_zm27p = 1; int gm_stall_us = 0; int ru_2line = 3; int cg_pbw = 5; int zm27_2line = 1;
-  int asm_fused = 1; int cg_pbws = 1; int scratch_cache = 1; int cb = 1;
+  int asm_fused = 1; int cg_pbws = 1; int scratch_cache = 1; int cb = 1; int zm_shared = 1;
   // fixed (the value each former key's A/B chose; DESIGN.md sections 4-11)
   static constexpr int spmv_nt = 1, spmv_grid = 0, dia = 1, jac_const = 1, cg_fold = 1, ws_skew = 0;
   static constexpr int cg_vec_grid = 0, cg_nts = 0, bnd_grid = 0, mask8 = 1, cg_upd_grid = 0, spmv_ynt = 0;
@@ -474,7 +474,8 @@ enum Dispatch {
   DSP_ZM_PBW = 15,       // CG mode 5: the direction update fused into the p.Ap pass (knob 69)
   DSP_ZM_PBWS = 16,      // CG mode 5 on P > 1 ranks: the same fused into the split p.Ap pass (knob 80)
   DSP_CB = 17,           // the column-block two-pass MatMult (mx_spmv_cb.hip, knob 84)
-  DSP_COUNT = 18
+  DSP_ZM_SHARED = 18,    // CG mode 5: a z-march pass whose workgroups share operands through LDS (knob 85; counted beside its pass's kind)
+  DSP_COUNT = 19
 };
 void note_dispatch(int kind);
 extern std::atomic<long long> g_dispatch[DSP_COUNT];

@@ -501,7 +501,12 @@ struct PairPbArgs {
   double c;                    // JM 2: the uniform Jacobi scalar
 };
 
-template <int PS, int JM, int B, int ZU>
+// XS (knob 85; 7-point): the workgroup's four waves hold four consecutive
+// columns of one segment and pass each plane's centre p_i through LDS -- the
+// +n operand is the centre pair of the wave one line on, the +1 edge lane 0
+// of the next unit's -- in place of the r and p_{i-1} loads that formed them
+// again: the owner's cg_dir of the same values, the same bits.
+template <int PS, int JM, int B, int ZU, bool XS = false>
 __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a, const int32_t *__restrict__ pblk,
                                                             const PairUni *__restrict__ puni, const PairPbArgs pa) {
   KspState *s = pa.s;
@@ -511,7 +516,7 @@ __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a
   if (blockIdx.x == 0 && threadIdx.x == 0) cg_commit_top(s, t, pa.hist);
   if (t.reason) return;
   const int i = t.i;
-  const double b = t.b;
+  double b = t.b;
   using SH = PairShape<PS>;
   constexpr int NR = SH::NR, TR = PS == 5 ? 1 : 2, LAST = NR - 1, C = SH::CENTER_RUN;
   auto pick = [&](int k) -> double * { return pa.pb + k * pa.ps; };
@@ -534,24 +539,50 @@ __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a
     se = a.S;
   }
   const __amdgpu_buffer_rsrc_t rr = vec_rsrc(rs, a.n), pr = vec_rsrc(pprev, a.n);
-  const int D = a.anchor[LAST];
+  int D = a.anchor[LAST];
   // the tri run's +1 edge: lane 63's x[ub + 128] (the backward edge is not
   // needed by the forward half); the other lanes load the same line
-  const int eoff = 128 + a.anchor[TR];
+  int eoff = 128 + a.anchor[TR];
+  double jc = pa.c;
+  if constexpr (XS) {
+    // the shared form is short of scalar registers (its uniform flags and LDS
+    // addresses beside two units' slot values): the uniform operands of
+    // vector arithmetic live in vector registers, so nothing spills
+    asm volatile("" : "+v"(b), "+v"(jc), "+v"(D), "+v"(eoff));
+  }
   constexpr uint32_t CARRY = PBLK_RUN0 | (PBLK_RUN0 << TR) | (PBLK_RUN0 << LAST);
   const int ntask = (se - sb) * a.P;
   double dot = 0.0;
+  static_assert(!XS || PS == 7, "shared form: 7-point");
+  // XS: the workgroup's exchange area, [buffer][wave][lane]; one barrier per
+  // plane: a buffer is written again two planes on, past the next plane's
+  // barrier, which every wave reaches with this plane's reads done
+  __shared__ dbl2 xch[XS ? 2 * LEAN_WAVES * 64 : 1];
+  const int PL = XS ? a.anchor[3] / 128 : 1;                 // XS: columns per line
+  // the lane's slot in the current buffer, the +n line's wave's, and lane 63's
+  // view of the next unit's lane 0 (vector registers: the pass is short of scalar ones)
+  int xw = wid * 64 + lane, xn = xw + PL * 64, xe = xw + 1;
   // NP: b == 0 (iteration 0, a restart), p_{i-1} not read
   auto march = [&](auto npc) __attribute__((always_inline)) {
     constexpr bool NP = decltype(npc)::value;
     auto dir = [&](dbl2 r2, dbl2 p2) __attribute__((always_inline)) {
-      return dbl2{cg_dir(jac1<JM>(r2.x, 0.0, pa.c), b, NP ? 0.0 : p2.x),
-                  cg_dir(jac1<JM>(r2.y, 0.0, pa.c), b, NP ? 0.0 : p2.y)};
+      return dbl2{cg_dir(jac1<JM>(r2.x, 0.0, jc), b, NP ? 0.0 : p2.x),
+                  cg_dir(jac1<JM>(r2.y, 0.0, jc), b, NP ? 0.0 : p2.y)};
     };
-    for (int tk = w; tk < ntask; tk += W) {
+    // the loop runs over the workgroup's group of four tasks (w - wid is a
+    // multiple of 4): XS has ntask a multiple of 4, so its trip count -- and
+    // the barriers inside -- are the same for the four waves
+    for (int tb = w - wid; tb < ntask; tb += W) {
+      const int tk = tb + wid;
+      if constexpr (!XS) { if (tk >= ntask) break; }
       const int seg = sb + tk / a.P, col = tk % a.P;
       const int z0 = seg * a.L, z1 = min(z0 + a.L, a.NZ);
       const int cb = col * 128 + 2 * lane;
+      // XS, wave-uniform (pair_cg5_pbw_launch: PL is 1, 2 or a multiple of 4, so the
+      // group is four lines, two lines of two units, or four units of a line):
+      // the +n line's wave and the next unit's are in the workgroup
+      const bool dnIn = XS && PL < 4 && wid + PL < LEAN_WAVES;
+      const bool hiIn = XS && wid < LEAN_WAVES - 1 && col % PL < PL - 1;
       dbl2 pc = dir(bload2(rr, z0 * D + cb), NP ? dbl2{0.0, 0.0} : bload2(pr, z0 * D + cb));   // p_i, centre
       uint32_t bwn = (uint32_t)pblk[z0 * a.P + col];
       auto step = [&](int z, auto nq) __attribute__((always_inline)) {
@@ -563,20 +594,25 @@ __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a
 #pragma unroll
         for (int q = 1; q < NQ; ++q) bw[q] = (uint32_t)pblk[(z + q) * a.P + col];
         if (z + NQ < z1) bwn = (uint32_t)pblk[(z + NQ) * a.P + col];
+        if constexpr (XS) xch[xw] = pc;                        // plane z's centre, for the workgroup
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
           const int r0 = (z + q) * D + cb, ub = (z + q) * D + col * 128;
           zr[q] = bload2(rr, r0 + D);
           zpp[q] = NP ? dbl2{0.0, 0.0} : bload2(pr, r0 + D);
           if constexpr (PS == 7) {
-            const int no = r0 + a.anchor[3] + ((bw[q] & (PBLK_RUN0 << 3)) ? PAIR_OOR : 0);
-            nr[q] = bload2(rr, no);
-            npp[q] = NP ? dbl2{0.0, 0.0} : bload2(pr, no);
+            nr[q] = dbl2{0.0, 0.0};
+            npp[q] = dbl2{0.0, 0.0};
+            if (!dnIn) {
+              const int no = r0 + a.anchor[3] + ((bw[q] & (PBLK_RUN0 << 3)) ? PAIR_OOR : 0);
+              nr[q] = bload2(rr, no);
+              npp[q] = NP ? dbl2{0.0, 0.0} : bload2(pr, no);
+            }
           }
           // a line's last unit has no +1 edge (wave-uniform: no loads)
           er[q] = 0.0;
           epp[q] = 0.0;
-          if (!(bw[q] & PBLK_EHI)) {
+          if (!(bw[q] & PBLK_EHI) && !hiIn) {
             er[q] = bload1(rr, ub + eoff);
             if constexpr (!NP) epp[q] = bload1(pr, ub + eoff);
           }
@@ -586,11 +622,21 @@ __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a
         for (int q = 0; q < NQ; ++q) {
           const int r0 = (z + q) * D + cb;
           const dbl2 pz = dir(zr[q], zpp[q]);
-          const double pe = cg_dir(jac1<JM>(er[q], 0.0, pa.c), b, NP ? 0.0 : epp[q]);
+          double pe = cg_dir(jac1<JM>(er[q], 0.0, jc), b, NP ? 0.0 : epp[q]);
           *reinterpret_cast<dbl2 *>(pout + r0) = pc;
           dbl2 L[NR];
           L[0] = dbl2{0.0, 0.0};                   // -D: not in the forward half
           if constexpr (PS == 7) { L[1] = dbl2{0.0, 0.0}; L[3] = dir(nr[q], npp[q]); }
+          if constexpr (XS && PS == 7) {
+            if (q > 0) xch[xw] = pc;                            // plane z + q's centre
+            __syncthreads();
+            // an empty +n run reads as 0.0, as its out-of-range loads' cg_dir does
+            // (defensive: in the layouts the host admits a plane's last line
+            // falls on waves with dnIn false, so the run is never empty here)
+            if (dnIn) L[3] = (bw[q] & (PBLK_RUN0 << 3)) ? dbl2{0.0, 0.0} : xch[xn];
+            if (hiIn && !(bw[q] & PBLK_EHI) && lane == 63) pe = xch[xe].x;   // the next unit's row 0
+            xw ^= LEAN_WAVES * 64; xn ^= LEAN_WAVES * 64; xe ^= LEAN_WAVES * 64;   // the other buffer
+          }
           L[TR] = pc;
           L[LAST] = pz;
           if (bw[q] & CARRY) {                     // wave-uniform, rare: an empty carried run
@@ -610,7 +656,7 @@ __global__ void __launch_bounds__(256) spmv_pair_pbw_kernel(const PairLeanArgs a
   };
   const std::true_type T{};
   const std::false_type F{};
-  if (b == 0.0) march(T);
+  if (t.b == 0.0) march(T);   // (the scalar copy: a uniform branch around the barriers)
   else march(F);
   double v[1] = {dot};
   block_partials<1>(v, a.partials, gridDim.x, a.fold);
@@ -2225,19 +2271,22 @@ static int cg5_args(const Mat *A, PairLeanArgs &a, int bpc = 0) {
 
 // knob 69: the fused direction update + p.Ap pass applies (one rank, a clean
 // symmetric 5/7-point z-march layout with the forward-half PW pass, no or a
-// uniform Jacobi, x batches of 2 or 4).  Default (5): by size -- 7-point up
-// to 2^23 rows, 5-point up to 2^24.  Per iteration, off -> on (tools/cg_ab.py,
-// gpurun_out/r4z, r4aa): 3D 128^3 37.3 -> 29.8 us, 256 x 128 x 128 57.2 ->
-// 48.7, 256 x 256 x 128 97.9 -> 90.1, 256 x 256 x 192 130.4 -> 131.9, 256^3
-// 173.4 -> 176.9; 2D 2048^2 55.6 -> 47.8, 4096 x 2048 97.4 -> 89.9, 4096^2
-// 170.2 -> 167.3, 8192 x 4096 353.3 -> 353.1.  While the vectors fit the
-// memory-side cache the saved pass is pure gain; at 256^3 the fused pass
-// saves 4.6 us (79.4 against 62.4 + 21.6) but the residual update after it
-// loses 5.2 (72.2 against 67.0: less of p_i left in that cache); reading the
-// +D streams non-temporally made it worse (176.5 / 181.0, r4y)
+// uniform Jacobi, x batches of 2, 4 or 8).  Default (5): by size, up to 2^24
+// rows.  Per iteration, off -> on unshared -> on with the shared form (knob
+// 85; tools/cg_ab.py, profiles/r07_zm_shared_ab.txt): 3D 128^3 40.2 -> 33.8 ->
+// 33.7 us, 256 x 256 x 128 104.9 -> 95.5 -> 94.9, 256 x 256 x 192 137.5 ->
+// 131.2 -> 129.2, 256^3 177.9 -> 175.9 -> 173.7 (the residual update after
+// the fused pass gives back 6 of the pass's gain there; plain bench.py, parent
+// against this rule, five runs each: 5619-5685 against 5745-6045 it/s).
+// (Round 4 measured 256^3 173.4 -> 176.9 with the unshared pass and kept
+// 7-point to 2^23 rows; 2D then: 2048^2 55.6 -> 47.8, 4096 x 2048 97.4 ->
+// 89.9, 4096^2 170.2 -> 167.3, 8192 x 4096 353.3 -> 353.1, unchanged here:
+// the 5-point pass has no shared form.)  x batches of 8 at 256^3 (knob 29;
+// fused on 7 of 8 iterations): 174.1 against 166.7 with batches of 4 -- the
+// default stays 4.
 bool pair_cg5_pbw_applies(const Mat *A, int jac_mode, int xb) {
   const int on = g_knobs.cg_pbw != 5 ? g_knobs.cg_pbw
-                                     : A->m <= (int64_t(1) << (A->sd.pair_shape == 5 ? 24 : 23));
+                                     : A->m <= (int64_t(1) << 24);
   return on && (xb == 2 || xb == 4 || xb == 8) && (jac_mode == 0 || jac_mode == 2) && pair_cg5_applies(A, jac_mode) &&
          A->sd.pair_shape != 27 && pair_lean_kind(A) == 2 && A->nghost == 0 && !A->sd.pair_ghosts && A->sym == 1 &&
          g_knobs.pw_sym27 && pair_zm_applies(A);
@@ -2274,6 +2323,22 @@ int pair_cg5_pbw_launch(Mat *A, KspState *s, const double *r, const double *r0, 
 #undef PBW_J
 #undef PBW_B
 #undef PBW
+  // knob 85: the shared form (7-point, two planes per step).  A workgroup's
+  // waves hold tasks 4g .. 4g + 3 of one XCD's slab; with the columns per plane
+  // a multiple of 4 those are one aligned group of four columns of one segment
+  // (the same planes: the same barriers), and with 1, 2 or a multiple of 4
+  // columns per line the group is whole lines or units of one line
+  const int NL = S.pair_shape == 7 ? a.anchor[3] : 0, PL = NL / 128;
+  if (g_knobs.zm_shared && z2 && NL > 0 && NL % 128 == 0 && D % NL == 0 && a.P % 4 == 0 &&
+      (PL == 1 || PL == 2 || PL % 4 == 0) && grid % 8 == 0) {
+#define PBWS(JM) do { if (xb == 8) f = &spmv_pair_pbw_kernel<7, JM, 8, 2, true>; \
+                      else if (xb == 4) f = &spmv_pair_pbw_kernel<7, JM, 4, 2, true>; \
+                      else f = &spmv_pair_pbw_kernel<7, JM, 2, 2, true>; } while (0)
+    if (jac_mode == 2) PBWS(2);
+    else PBWS(0);
+#undef PBWS
+    note_dispatch(DSP_ZM_SHARED);
+  }
   note_dispatch(DSP_ZM_PBW);
   launch_timed(f, grid, st, a, S.pblk.p, S.puni.p, pa);
   HIPCHECK(hipGetLastError());

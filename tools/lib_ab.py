@@ -4,6 +4,8 @@ RTLD_LOCAL, so each keeps its own kernels and knobs): interleaved CG rounds
 on the same device, so placement, clocks and neighbours hit both alike.
 
     python tools/lib_ab.py libA.so,libB.so[,...] [n] [rounds] [knob=value+...]
+A path may carry knobs of its own, libA.so@85=0+69=1 (set after the common
+ones): two copies of one build under two file names then A/B a key.
 AB_KIND (stencil kind, default 1 = 3D 7-pt; 3 = conv-diff) and AB_KSP
 (0 = CG, 1 = GMRES(30)) select the operator and the method.
 """
@@ -20,9 +22,12 @@ ksp = int(os.environ.get("AB_KSP", "0"))
 knobs = [tuple(int(u) for u in kv.split("=")) for kv in sys.argv[4].split("+")] if len(sys.argv) > 4 else []
 torch.cuda.init()
 libs = []
-for pth in paths:
+own = [[tuple(int(u) for u in kv.split("=")) for kv in p.split("@")[1].split("+")] if "@" in p else [] for p in paths]
+labels = [os.path.basename(p) for p in paths]
+paths = [p.split("@")[0] for p in paths]
+for pth, kn in zip(paths, own):
     L = C.CDLL(os.path.abspath(pth), mode=os.RTLD_LOCAL)
-    for k, v in knobs:
+    for k, v in knobs + kn:
         L.mx_debug_set(k, v)
     comm, A = C.c_void_p(), C.c_void_p()
     assert L.mx_comm_create_self(0, C.byref(comm)) == 0
@@ -56,6 +61,6 @@ for rnd in range(rounds):
         solve(libs[j], 300)
         torch.cuda.synchronize(); res[j].append((time.perf_counter() - t0) / 300 * 1e6)
 print(json.dumps({"n": n, "kind": kind, "ksp": ksp, "knobs": sys.argv[4] if len(sys.argv) > 4 else "",
-                  **{f"{j}:{os.path.basename(p)}": {"med_us": round(float(np.median(t)), 1),
+                  **{f"{j}:{p}": {"med_us": round(float(np.median(t)), 1),
                                                     "all": [round(v, 1) for v in t]}
-                     for j, (p, t) in enumerate(zip(paths, res))}}), flush=True)
+                     for j, (p, t) in enumerate(zip(labels, res))}}), flush=True)
