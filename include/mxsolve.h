@@ -46,7 +46,7 @@ typedef struct mx_comm_s *mx_comm;
 typedef struct mx_mat_s *mx_mat;
 
 /* ---- KSP parameters / results (KSPSetType, KSPSetTolerances, PCSetType) ---- */
-enum { MX_KSP_CG = 0, MX_KSP_GMRES = 1, MX_KSP_PREONLY = 2 };
+enum { MX_KSP_CG = 0, MX_KSP_GMRES = 1, MX_KSP_PREONLY = 2, MX_KSP_BCGS = 3 };
 enum { MX_PC_NONE = 0, MX_PC_JACOBI = 1 };
 enum { MX_NORM_DEFAULT = -1, MX_NORM_NONE = 0, MX_NORM_PRECONDITIONED = 1,
        MX_NORM_UNPRECONDITIONED = 2, MX_NORM_NATURAL = 3 };
@@ -69,7 +69,10 @@ typedef struct {
                           direction-update launch with batched x steps (cg_pb_kernel)
                           / GMRES MAXPY + norm; bit 3: every CG fused direction +
                           p.Ap pass (one rank: events attached to the kernel's
-                          dispatch)                                                  */
+                          dispatch).  BiCGStab: bit 0 both MatMults of every
+                          iteration (spmv_ms / spmv_count), bit 1 the x / R update
+                          pass bcgs_xr (upd_ms / upd_count), bit 2 the direction
+                          update bcgs_p (pb_ms / pb_count)                           */
 } mx_ksp_params;
 
 typedef struct {
@@ -265,7 +268,17 @@ int mx_vec_maxpy(mx_comm c, int64_t n, double *y_dev, int nv, const double *alph
 int mx_vec_rhs_hash(mx_comm c, int64_t i0, int64_t n, double *b_dev);
 
 /* ---- KSP: replaces ksp.solve(b, x) (test.py:50) -> KSPSolve with the
- *      configuration of test.py:33-47 + options.  [collective]              */
+ *      configuration of test.py:33-47 + options.  [collective]
+ * MX_KSP_BCGS (KSPBCGS, BiCGStab): left preconditioning (MX_PC_NONE or
+ * MX_PC_JACOBI), the preconditioned residual norm (MX_NORM_DEFAULT /
+ * MX_NORM_PRECONDITIONED; MX_NORM_NONE skips the test and stops at max_it with
+ * CONVERGED_ITS; MX_NORM_UNPRECONDITIONED / MX_NORM_NATURAL fail with
+ * MX_ERR_UNSUPPORTED).  Seven work vectors, two MatMults and five vector
+ * passes per iteration, no restart; its recurrences (rho, alpha, omega, beta)
+ * stay on the device.  Reason DIVERGED_BREAKDOWN (-5): rho = RP . R or
+ * V . RP is exactly zero (x and its as before that iteration), or T = B A S
+ * vanished with S != 0 (after x += alpha P); T and S both zero is
+ * CONVERGED_RTOL with a residual norm of 0.                                  */
 int mx_ksp_solve(mx_mat A, const mx_ksp_params *p, const double *b_dev, double *x_dev,
                  mx_ksp_result *res, double *history_host /* NULL or max_it+2 */);
 void mx_ksp_default_params(mx_ksp_params *p);

@@ -47,6 +47,19 @@ struct CgTopIn {
   int xlo, xhi;
 };
 
+// BiCGStab's scalar recurrence (mx_bcgs.hpp).  Written by one thread after
+// the reduction that feeds it, read by the passes of later launches.
+struct BcgsState {
+  double rho;               // RP . R of the iteration about to run
+  double beta;              // (rho / rhoold) (alphaold / omegaold); unused at iteration 0
+  double d1;                // V . RP (alpha = rho / d1, evaluated where it is used)
+  double omega;             // (S . T) / (T . T); the previous iteration's until bcgs_dot2 ran
+  double ss;                // S . S, kept for the T == 0 exit
+  double dp;                // || R ||
+  int it;                   // iteration about to run (== its)
+  int tzero;                // T vanished: the last pass applies x += alpha P only and stops
+};
+
 // Device-resident solver state (one allocation, zeroed then parameterised at
 // every solve, which also clears the in-launch fold counters).
 struct KspState {
@@ -63,6 +76,7 @@ struct KspState {
   double pb;
   double red1;              // CG p.w (folded, then all-reduced)
   double dpis[2];           // parity slots: dpi_i in dpis[i & 1]
+  BcgsState bc;
   alignas(128) CgTopIn top;
   // in-launch fold counters (Fold, mx_device.hpp), one 256-B line each: the
   // p.w partials of the MatMult and the update pass's [z.z, z.r, r.r]

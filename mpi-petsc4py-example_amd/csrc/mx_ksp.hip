@@ -1,4 +1,5 @@
-// mx_ksp.hip -- KSPSolve on gfx950: CG, GMRES(restart) and PREONLY with Jacobi.
+// mx_ksp.hip -- KSPSolve on gfx950: CG, GMRES(restart), BiCGStab (mx_bcgs.hpp)
+// and PREONLY with Jacobi.
 //
 // Replaces ksp.solve(b, x) (test.py:50) under -ksp_type cg|gmres|preonly
 // -pc_type jacobi|none.  The algorithms,
@@ -1896,6 +1897,8 @@ static void gmres_solve(Mat *A, const mx_ksp_params &p, const Jac dinv, const do
   if (hist_host) HIPCHECK(hipMemcpy(hist_host, hist.p, sizeof(double) * ((size_t)hs.its + 1), hipMemcpyDeviceToHost));
 }
 
+#include "mx_bcgs.hpp"   // KSPBCGS: its kernels and bcgs_solve
+
 void ksp_solve(Mat *A, const mx_ksp_params &p, const double *b, double *x, mx_ksp_result &r,
                double *hist) {
   std::memset(&r, 0, sizeof(r));
@@ -1935,6 +1938,7 @@ void ksp_solve(Mat *A, const mx_ksp_params &p, const double *b, double *x, mx_ks
   switch (p.ksp_type) {
     case MX_KSP_CG: cg_solve(A, p, dv, b, x, r, hist); break;
     case MX_KSP_GMRES: gmres_solve(A, p, dv, b, x, r, hist); break;
+    case MX_KSP_BCGS: bcgs_solve(A, p, dv, b, x, r, hist); break;
     case MX_KSP_PREONLY:   // KSPSolve_PREONLY: x = B b, its = 1, CONVERGED_ITS
       if (dv.mode) vec_pmult(st, n, b, A->jac_dinv.p, x);
       else if (n) HIPCHECK(hipMemcpyAsync(x, b, sizeof(double) * n, hipMemcpyDeviceToDevice, st));

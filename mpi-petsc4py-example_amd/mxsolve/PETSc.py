@@ -1117,8 +1117,8 @@ class KSP:
             self._timing = {"KSPSolve": time.perf_counter() - t0}
             self._report()
             return
-        if kt not in ("cg", "gmres", "preonly"):
-            raise Error(PETSC_ERR_SUP, f"KSP type {kt} is not on the GPU path (cg, gmres, preonly)")
+        if kt not in ("cg", "gmres", "bcgs", "preonly"):
+            raise Error(PETSC_ERR_SUP, f"KSP type {kt} is not on the GPU path (cg, gmres, bcgs, preonly)")
         if pct not in ("jacobi", "none"):
             raise Error(PETSC_ERR_SUP, f"PC type {pct} is not on the GPU path (jacobi, none; lu with preonly)")
         h = self._A.getDeviceHandle()

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._lib import KSPParams, KSPResult, MatInfo, MxError, call
 
-KSP_TYPES = {"cg": 0, "gmres": 1, "preonly": 2}
+KSP_TYPES = {"cg": 0, "gmres": 1, "preonly": 2, "bcgs": 3}
 PC_TYPES = {"none": 0, "jacobi": 1}
 NORM_TYPES = {"default": -1, "none": 0, "preconditioned": 1, "unpreconditioned": 2, "natural": 3}
 STENCILS = {"poisson2d": 0, "poisson3d": 1, "poisson3d27": 2, "convdiff3d": 3}
